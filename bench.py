@@ -22,6 +22,17 @@ WORLD_SIZE and must equal --gpus (else exit 2).  `python bench.py --gpus N` with
 N fresh rank processes through torch.distributed.run itself (before any GPU call) and exits with
 their status.  The JSON line reports the world size the process group saw.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+line: metric, value, ms_per_step, the step's config and loss.  `--full` adds everything that takes work
+of its own: the HIP-event probes on the last tenth of the timed steps and the per-kernel roofline objects
+built from them, the hipGraph timing of the HBM-bound kernels, and the CPU-oracle baseline
+(`--no-probe` / `--no-cpu-baseline` drop single legs of a `--full` run).
+
+`--dump-outputs DIR` writes what the last timed step left for its caller as DIR/<name>.npy (float32 /
+float64): the step's loss and correct-count vectors, the DP parameter, and a fixed, seeded sample of the
+stepped fp32 master weights and of the model Adam's two moments.  Seeds, inputs and dropout streams are
+fixed, so two builds run with the same arguments can be compared array for array.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -109,9 +120,15 @@ def parse_args(argv=None):
     ap.add_argument("--eps-sweep", default="", help="comma-separated eps values (configs[4]: 0.1,1,3,5,10)")
     ap.add_argument("--eps-mode", default="newfrac", choices=["newfrac", "new"])
     ap.add_argument("--feawei", type=int, default=0, help="feawei feature pass over this many synthetic samples")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the HIP-event probes and the "
+                         "per-kernel roofline, the hipGraph timing of the HBM-bound kernels, the CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU-oracle baseline leg")
     ap.add_argument("--no-probe", action="store_true",
-                    help="no HIP-event probes in the timed loop (no per-kernel roofline; A/B of the probes' cost)")
+                    help="with --full: no HIP-event probes in the timed loop (no per-kernel roofline; A/B of the "
+                         "probes' cost)")
     ap.add_argument("--cpu-batch", type=int, default=256,
                     help="CPU-baseline batch (BASELINE.md section 3: the bench's batch, 256; ~107 s per iteration "
                          "on a GPU box's 16-CPU share)")
@@ -407,6 +424,40 @@ def probe_stats(probe: dict) -> dict:
     return out
 
 
+DUMP_SAMPLE = 1 << 21             # elements per sampled array: 8 MB of float32 each, three of them
+
+
+def dump_outputs(out_dir: str, eng, trainer, loss, correct) -> dict:
+    """What the last timed step left for its caller, as <out_dir>/<name>.npy: the loss and correct-count
+    vectors it returned, the DP parameter, and the same seeded sample (numpy default_rng(0), sorted
+    positions inside the sub-ranges Adam steps) of the fp32 master weights and of the model Adam's first and
+    second moments.  Returns name -> [shape, dtype] for the result line."""
+    import numpy as np
+    import torch
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    opt = getattr(trainer, "model_opt", None) or trainer.opt
+    lens = np.array([hi - lo for lo, hi in opt.sub], dtype=np.int64)
+    ends = np.cumsum(lens)
+    pos = np.sort(np.random.default_rng(0).integers(0, int(ends[-1]), size=min(DUMP_SAMPLE, int(ends[-1]))))
+    k = np.searchsorted(ends, pos, side="right")
+    arena_idx = np.array([lo for lo, _ in opt.sub], dtype=np.int64)[k] + (pos - (ends - lens)[k])
+    idx = torch.from_numpy(arena_idx).to(eng.a.master.device)
+    arrays = {"loss": loss.detach().double().cpu().numpy(),
+              "correct": correct.detach().double().cpu().numpy(),
+              "master_sample": eng.a.master[idx].float().cpu().numpy(),
+              "adam_m_sample": opt.m[idx - opt.lo].float().cpu().numpy(),
+              "adam_v_sample": opt.v[idx - opt.lo].float().cpu().numpy()}
+    dp_opt = getattr(trainer, "dp_opt", None)
+    if dp_opt is not None:
+        arrays["dp"] = eng.a.master[dp_opt.lo:dp_opt.hi].float().cpu().numpy()
+        arrays["dp_adam_m"] = dp_opt.m.float().cpu().numpy()
+    for name, arr in arrays.items():
+        np.save(d / f"{name}.npy", arr)
+    return {name: [list(arr.shape), str(arr.dtype)] for name, arr in arrays.items()}
+
+
 def main():
     args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
@@ -512,7 +563,8 @@ def main():
         feawei = {"samples": acc.count, "seconds": round(time.perf_counter() - t0, 3), "k": 1.0, "zscore": True}
 
     tags = tuple(KERNEL_GROUPS)
-    total_dt, per_eps, loss = 0.0, [], None
+    probing = args.full and not args.no_probe
+    total_dt, per_eps, loss, correct = 0.0, [], None, None
     probe_all = {t: [] for t in tags}
     for eps in sweep:
         eng.cfg.eps = eps
@@ -526,7 +578,7 @@ def main():
         # profiles/r5l_probe_cost.log), so they are live only on the last steps of the timed region
         # (one in ten, at least one): the per-kernel averages come from the timed region, and the
         # step time carries ~0.1 ms of probe cost per step instead of 1.3
-        n_probe = 0 if args.no_probe else max(1, args.steps // 10)
+        n_probe = max(1, args.steps // 10) if probing else 0
         probe_on = {t: [] for t in tags}
         eng.probe = None
         torch.cuda.synchronize()
@@ -536,7 +588,7 @@ def main():
         for i in range(args.steps):
             if i == args.steps - n_probe:
                 eng.probe = probe_on
-            loss, _ = trainer.step(batch, labels)
+            loss, correct = trainer.step(batch, labels)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -554,13 +606,17 @@ def main():
 
     # the small HBM-bound kernels timed by hipGraph replay (after the timed region; no effect on value)
     hbm_times = {}
-    if world == 1 and not args.no_probe:
+    if world == 1 and probing:
         try:
             adam_elems = sum(hi - lo for lo, hi in trainer.model_opt.sub) if hasattr(trainer, "model_opt") else \
                 sum(hi - lo for lo, hi in trainer.opt.sub)
             hbm_times = hbm_kernel_graph_times(dev, B, adam_elems, eng.cfg.seed)
         except Exception as exc:          # a diagnostic leg: report, never fail the bench line
             print(f"[bench] hbm kernel graph timing failed: {exc!r}", file=sys.stderr)
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, eng, trainer, loss, correct)
 
     replicas = None
     if args.check_replicas:
@@ -579,7 +635,7 @@ def main():
 
     if rank == 0:
         steps = args.steps * len(sweep)
-        probed_steps = max(1, (0 if args.no_probe else max(1, args.steps // 10)) * len(sweep))
+        probed_steps = max(1, (max(1, args.steps // 10) if probing else 0) * len(sweep))
         value = world * B * steps / total_dt
         ks = probe_stats(probe_all)
         step_tf = value / world * flops_per_sample(args.variant) / 1e12
@@ -683,12 +739,18 @@ def main():
             "hbm_kernels": hbm,
             "loss": float(loss[-1].item()),
         }
+        if not args.full:
+            # a plain run probes nothing: the per-kernel objects belong to --full
+            for k in ("roofline", "roofline_ffn1", "kernels", "kernels_by_symbol", "hbm_kernels"):
+                del out[k]
         if len(sweep) > 1 or feawei is not None:
             out["sweep"] = per_eps
             out["feawei"] = feawei
         if replicas is not None:
             out["replicas"] = replicas
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # batch 256 (the GPU leg's batch), 1 warm-up + 3 timed iterations, in this run;
             # the stderr heartbeat every 30 s keeps the ~5.5 min leg visibly alive
             cb = cpu_baseline(args.variant, args.cpu_batch, args.cpu_iters, args.cpu_warm_batch, args.cpu_budget)

@@ -1,6 +1,6 @@
 """Contract T pad skipping: BERT over the packed real tokens of right-padded
 sequences must give the padded computation's outputs (the reference masks padded keys,
-/root/reference/model.py:37-43; padded query rows never reach the loss).
+its model.py:37-43; padded query rows never reach the loss).
 
 Checks, all through the C-ABI:
   * eegf_attn_varlen_fwd/bwd against the dense kernels on the padded layout with the key mask
