@@ -70,6 +70,9 @@ SIGNATURES: dict[str, list] = {
     "eegf_tanh_bwd": [i32, i64, vp, vp, vp, vp],
     "eegf_key_bias": [i64, vp, vp, vp],
     "eegf_window_tokens": [i32, i32, i32, i32, vp, vp, vp],
+    "eegf_window_patch_tokens": [i32, i32, i32, i32, i32, vp, vp, i64, i64, vp, vp, vp],
+    "eegf_window_token_mask": [i32, i32, i32, vp, vp, vp],
+    "eegf_packed_pos_rows": [i32, i32, i32, vp, i64, i64, vp, vp, vp],
     "eegf_embed_gather": [i32, i64, i32, vp, vp, vp, vp],
     "eegf_embed_scatter_add": [i32, i64, i32, vp, vp, vp, vp],
     "eegf_v1_gate_fwd": [i32, vp, i64, vp, vp, vp, f32, i32, f32, u64, u64, vp, vp, vp, vp, vp, vp],

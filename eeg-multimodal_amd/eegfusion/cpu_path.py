@@ -45,10 +45,24 @@ def _bert(model, cfg, batch, training):
     emb = bert.embeddings
     p_h, p_a = (cfg.hidden_dropout, cfg.attn_dropout) if training else (0.0, 0.0)
     if cfg.contract == "W":
+        from .engine import window_geometry
         eeg = batch["eeg"]                                           # [B, C, T] channel x time
-        x = _lin(eeg.transpose(1, 2), model.eeg_encoder)             # time-major tokens -> inputs_embeds
-        B, L = x.shape[:2]
+        steps, patch = batch.get("eeg_mask"), cfg.eeg_patch
+        B, C, T = eeg.shape
+        L = window_geometry(patch, B, C, T, steps)
+        if steps is not None:                                        # masked steps read as 0 (never as NaN)
+            steps = steps != 0
+            eeg = torch.where(steps[:, None, :], eeg, torch.zeros((), dtype=eeg.dtype))
+        tokens = eeg.transpose(1, 2)                                 # time-major tokens [B, T, C]
+        if patch > 1:                                                # token j: column c*P + p = channel c, step jP + p
+            tokens = eeg.view(B, C, L, patch).permute(0, 2, 1, 3).reshape(B, L, C * patch)
+        x = _lin(tokens, model.eeg_encoder)                          # -> inputs_embeds
         mask = torch.ones(B, L, dtype=torch.long)
+        if steps is not None:                                        # a token is valid when any of its steps is
+            mask = steps.view(B, L, patch).any(-1).long()
+            if not bool(mask.any(1).all()):
+                raise ValueError("eegfusion: an eeg_mask row has no valid token (the decoder's softmax over an "
+                                 "empty memory is NaN)")
     else:
         ids, mask = batch["title_input"], batch["text_mask"]
         lens = mask.sum(1)

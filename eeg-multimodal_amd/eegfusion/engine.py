@@ -49,6 +49,29 @@ def P(t):
     return None if t is None else t.data_ptr()
 
 
+PATCHES = (1, 2, 4, 8)
+MAX_POS = 512                     # rows of bert.embeddings.position_embeddings
+
+
+def window_geometry(patch: int, B: int, C: int, T: int, mask=None) -> int:
+    """Contract W shape checks (host only, before any launch): -> the token count L = T / patch.
+    mask: the step mask [B, T] or None."""
+    if patch not in PATCHES:
+        raise ValueError(f"eegfusion: eeg_patch must be one of {PATCHES}, got {patch!r}")
+    if patch > 1 and (C * patch > 1024 or (C * patch) % 8):
+        raise ValueError(f"eegfusion: patch rows of {C} channels x {patch} steps = {C * patch} elements "
+                         "(at most 1024, a multiple of 8)")
+    if T <= 0 or T % patch:
+        raise ValueError(f"eegfusion: window length {T} is not a multiple of eeg_patch {patch}")
+    L = T // patch
+    if L > MAX_POS:
+        raise ValueError(f"eegfusion: {L} tokens per window (T {T} / eeg_patch {patch}) exceed the {MAX_POS} "
+                         "position embeddings; use a larger eeg_patch")
+    if mask is not None and tuple(mask.shape) != (B, T):
+        raise ValueError(f"eegfusion: eeg_mask must be [B, T] = [{B}, {T}], got {list(mask.shape)}")
+    return L
+
+
 @dataclass
 class EngineConfig:
     contract: str = "W"            # "W" window / "T" token ids
@@ -60,6 +83,7 @@ class EngineConfig:
     attn_dropout: float = 0.1      # BertConfig.attention_probs_dropout_prob (fused into eegf_attn_*)
     dec_dropout: float = 0.1       # TransformerDecoderLayer(dropout=0.1)
     eeg_channels: int = 64
+    eeg_patch: int = 1             # contract W: time steps per token (Conv1d(C, 768, kernel P, stride P) as a GEMM)
     act_dim: int = 32
     seed: int = 980616
     tau: float = 1.0               # PriGumbel-v1 gumbel_softmax temperature (train_val.py:95)
@@ -612,15 +636,59 @@ class FusionEngine:
         T = int(cu[-1])
         return dict(cu=torch.from_numpy(cu).to(dev), T=T, rows=(T + 255) // 256 * 256, max_len=int(lens.max()))
 
+    def _window_plan(self, mask, B, T, patch, L):
+        """Contract W step mask [B, T] (nonzero = valid) -> the plan of the batch: the int64 step mask the
+        token kernel reads, the any-valid token mask, its key bias, the per-row token counts / cu_seqlens
+        and whether every row is a prefix (one device pass, one small D2H copy, as _varlen_plan).  Made
+        once per mask tensor: a trainer step's second forward on the same batch reuses it."""
+        hit = getattr(self, "_wplan", None)
+        if hit is not None and hit[0] is mask and hit[1] == mask._version and hit[2] == (B, T, patch):
+            return hit[3]
+        dev = self.a.device
+        steps = mask if mask.dtype == torch.int64 and mask.is_contiguous() else mask.ne(0).to(torch.int64).contiguous()
+        if patch == 1:
+            tmask = steps
+        else:
+            tmask = torch.empty(B, L, dtype=torch.int64, device=dev)
+            call("eegf_window_token_mask", B, T, patch, P(steps), P(tmask), _stream())
+        buf = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        call("eegf_seq_lengths", B, L, P(tmask), P(buf), P(buf[B:]), _stream())
+        host = buf.cpu().numpy()
+        lens = host[:B].astype(np.int64)
+        if lens.min() <= 0:
+            raise ValueError(f"eegfusion: eeg_mask row {int(lens.argmin())} has no valid token (the decoder's "
+                             "softmax over an empty memory is NaN)")
+        plan = dict(steps=steps, full=bool((lens == L).all()), prefix=host[B] == 0, kbias=None, vl=None)
+        if not plan["full"]:
+            plan["kbias"] = torch.empty(B, L, dtype=torch.float32, device=dev)
+            call("eegf_key_bias", B * L, P(tmask), P(plan["kbias"]), _stream())
+            if plan["prefix"]:
+                cu = np.zeros(B + 1, dtype=np.int32)
+                cu[1:] = np.cumsum(lens)
+                n = int(cu[-1])
+                plan["vl"] = dict(cu=torch.from_numpy(cu).to(dev), T=n, rows=(n + 255) // 256 * 256,
+                                  max_len=int(lens.max()))
+        self._wplan = (mask, mask._version, (B, T, patch), plan)
+        return plan
+
     # =================================================================== forward
     def forward(self, batch: dict, hard: bool, training: bool, save: bool = True):
-        """batch (device tensors): contract W: eeg [B,C,T] f32, act [B,A] f32;
+        """batch (device tensors): contract W: eeg [B,C,T] f32, act [B,A] f32, optionally eeg_mask [B,T]
+        (integer / bool, nonzero = valid step; DESIGN §3.4);
         contract T: title_input [B,L] i64, text_mask [B,L] i64, frame_input [B,1,512] f32 (the modality
         variants add title_input2 / text_mask2 (TTCA) or frame_input2 (IICA), MODALS)."""
         cfg = self.cfg
+        wplan = None
+        if cfg.contract == "W":
+            # shape checks and the mask plan first: a refused window launches nothing of the model
+            eeg, emask = batch["eeg"], batch.get("eeg_mask")
+            Lw = window_geometry(cfg.eeg_patch, eeg.shape[0], eeg.shape[1], eeg.shape[2], emask)
+            if emask is not None:
+                wplan = self._window_plan(emask, eeg.shape[0], eeg.shape[2], cfg.eeg_patch, Lw)
         self._refresh_shadow()
         sv = Saved(hard=hard, training=training)
         t = sv.t
+        t["wplan"] = wplan
         sv.rng = self.rng_counter
         self.rng_counter += 1 << 12
         ddrop = cfg.dec_dropout if training else 0.0
@@ -686,13 +754,36 @@ class FusionEngine:
         # ---------------- EEG front-end + BERT embeddings
         if cfg.contract == "W":
             eeg = batch["eeg"]
-            B, C, L = eeg.shape
-            tok = self.empty(B * L, C)
-            call("eegf_window_tokens", self.code, B, C, L, P(eeg), P(tok), _stream())
-            x = self.empty(B * L, HID)
-            self.linear(tok, self.W("eeg_encoder.weight"), self.F("eeg_encoder.bias"), x, B * L)
-            kbias = None
+            B, C, Tn = eeg.shape
+            patch = cfg.eeg_patch
+            L = Tn // patch
+            plan = t.get("wplan")
+            if plan is not None and plan["full"] and patch == 1:
+                plan = None            # every step valid: the unmasked batch, launch for launch
+            kbias = plan["kbias"] if plan is not None else None
+            vl = None
+            if kbias is not None and plan["vl"] is not None and cfg.varlen and self.psn is None:
+                vl = plan["vl"]        # prefix rows: BERT over the packed valid tokens (pad skipping)
+            elif L % 256:
+                # lengths the dense attention kernels do not take: the padded layout on the varlen kernels
+                vl = self._uniform_plan(B, L, kbias)
+            packed = vl is not None and not vl.get("uniform")
+            R = vl["rows"] if packed else B * L
+            tok = self.empty(R, C * patch)
+            if plan is None and patch == 1 and vl is None:
+                call("eegf_window_tokens", self.code, B, C, L, P(eeg), P(tok), _stream())
+            else:
+                call("eegf_window_patch_tokens", self.code, B, C, Tn, patch,
+                     P(plan["steps"]) if plan is not None else None, P(vl["cu"]) if packed else None,
+                     vl["T"] if packed else B * L, R, P(eeg), P(tok), _stream())
+            x = self.empty(R, HID)
+            self.linear(tok, self.W("eeg_encoder.weight"), self.F("eeg_encoder.bias"), x, R)
+            if packed:                 # position row j for packed row cu[b] + j: the LayerNorm's fp32 table
+                t["pos_rows"] = self._f32(R, HID)
+                call("eegf_packed_pos_rows", B, L, HID, P(vl["cu"]), vl["T"], R,
+                     P(self.F("bert.embeddings.position_embeddings.weight")), P(t["pos_rows"]), _stream())
             t["tok"] = tok
+            sv.vl = vl
         else:
             ids = batch["title_input"]
             B, L = ids.shape
@@ -737,10 +828,13 @@ class FusionEngine:
         # the FFN pre-activations are not stored
         s0, m0, r0 = (self.empty(R, HID), self._f32(R), self._f32(R)) if save else (None, None, None)
         # position rows: the LN table add (dense) or already in the packed gather (varlen)
+        # (contract T), or the packed position rows as the table (contract W: eegf_packed_pos_rows)
         packed = vl is not None and not vl.get("uniform")
+        pos_rows = t.pop("pos_rows", None)
         self.ln_fwd(x, None, e + "LayerNorm", R, h, s0, m0, r0, 1e-12, pdrop, 2, sv.rng + 1,
-                    table=None if packed else self.F(e + "position_embeddings.weight"),
-                    period=1 if packed else L, table2=self.F(e + "token_type_embeddings.weight"))
+                    table=(pos_rows if packed else self.F(e + "position_embeddings.weight")),
+                    period=(R if pos_rows is not None else 1) if packed else L,
+                    table2=self.F(e + "token_type_embeddings.weight"))
         t["emb"] = (s0, m0, r0)
         scale = DH ** -0.5
 

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from .arena import ParamArena
-from .engine import DEC_FF, DEC_L, FFN, FUSED, HID, NL, EngineConfig, FusionEngine
+from .engine import DEC_FF, DEC_L, FFN, FUSED, HID, NL, EngineConfig, FusionEngine, window_geometry
 
 # ------------------------------------------------------------------- name-holding modules
 
@@ -164,7 +164,7 @@ class FusionModel(nn.Module):
     def __init__(self, variant: str, contract: str = "T", eps: float = 1.0, eps_mode: str = "newfrac",
                  dtype: torch.dtype = torch.float32, eeg_channels: int = 64, act_dim: int = 32, frame_dim: int = 512,
                  with_dp: bool = True, dp_init: torch.Tensor | None = None, dropout: float = 0.1, seed: int = 980616,
-                 tau: float = 1.0, modal: str = "ti", host_path: bool = False):
+                 tau: float = 1.0, modal: str = "ti", host_path: bool = False, eeg_patch: int = 1):
         super().__init__()
         self._variant, self._contract, self._modal = variant, contract, modal
         # host_path=True: run the torch-op host path (cpu_path) while the model is in host memory even
@@ -176,7 +176,10 @@ class FusionModel(nn.Module):
             self.bert = _bert()
             _init_bert_(self.bert)
         if contract == "W":
-            self.eeg_encoder = nn.Linear(eeg_channels, HID)
+            # eeg_patch P > 1: a patch tokenizer, one token per P time steps.  weight.view(768, C, P) is the
+            # Conv1d(C, 768, kernel P, stride P) weight (column c*P + p: channel c, step p of the patch)
+            window_geometry(eeg_patch, 1, eeg_channels, eeg_patch)
+            self.eeg_encoder = nn.Linear(eeg_channels * eeg_patch, HID)
             self.visual_encoder = nn.Linear(act_dim, HID)
         elif modal != "tt":
             self.visual_encoder = nn.Linear(frame_dim, HID)
@@ -206,7 +209,8 @@ class FusionModel(nn.Module):
         self.eps = torch.tensor(eps)
         self._cfg = EngineConfig(contract=contract, variant=variant, dtype=dtype, eps=float(eps), eps_mode=eps_mode,
                                  hidden_dropout=dropout, attn_dropout=dropout, dec_dropout=dropout,
-                                 eeg_channels=eeg_channels, act_dim=act_dim, seed=seed, tau=float(tau), modal=modal)
+                                 eeg_channels=eeg_channels, act_dim=act_dim, seed=seed, tau=float(tau), modal=modal,
+                                 eeg_patch=int(eeg_patch))
         self._build_arena(torch.device("cpu"))
         self._dp = None                      # DP-SGD state (eegfusion.dpsgd.GradSampleModule)
 
@@ -318,9 +322,17 @@ class FusionModel(nn.Module):
                 p.grad = a.gview(n)
         eng.needs_grad = None
 
-    def forward_window(self, eeg: torch.Tensor, act: torch.Tensor, hard: bool = True) -> torch.Tensor:
-        """Contract W: eeg [B, C, T] (channel x time) fp32, act [B, A] fp32 -> logits [B, 2]."""
-        return self._run({"eeg": eeg.contiguous().float(), "act": act.contiguous().float()}, hard)
+    def forward_window(self, eeg: torch.Tensor, act: torch.Tensor, hard: bool = True,
+                       eeg_mask: torch.Tensor | None = None) -> torch.Tensor:
+        """Contract W: eeg [B, C, T] (channel x time) fp32, act [B, A] fp32 -> logits [B, 2].
+        T / eeg_patch tokens (at most 512), any length.  eeg_mask [B, T] (integer or bool, nonzero = valid
+        step; None = all valid): masked steps read as 0, a token is valid when any of its steps is, invalid
+        tokens are masked as BERT keys and as decoder memory (the oracle's batch["eeg_mask"])."""
+        window_geometry(self._cfg.eeg_patch, eeg.shape[0], eeg.shape[1], eeg.shape[2], eeg_mask)
+        batch = {"eeg": eeg.contiguous().float(), "act": act.contiguous().float()}
+        if eeg_mask is not None:
+            batch["eeg_mask"] = eeg_mask
+        return self._run(batch, hard)
 
     def _token_batch(self, frame_input, vedio_mask, title_input, text_mask):
         if self._contract == "W":
@@ -517,9 +529,9 @@ class PriGumbelV1Model(FusionModel):
         self._engine.cfg.tau = float(self.dropout.tau)
         return self._run(self._token_batch(frame_input, vedio_mask, title_input, text_mask), not self.training)
 
-    def forward_window(self, eeg, act, hard=None):
+    def forward_window(self, eeg, act, hard=None, eeg_mask=None):
         self._engine.cfg.tau = float(self.dropout.tau)
-        return super().forward_window(eeg, act, (not self.training) if hard is None else hard)
+        return super().forward_window(eeg, act, (not self.training) if hard is None else hard, eeg_mask)
 
 
 def load_bert_weights(model: FusionModel, path: str):

@@ -318,6 +318,26 @@ int eegf_key_bias(long n, const long long* mask, float* bias, hipStream_t stream
 
 /* EEG window [B,C,T] fp32 (channel x time) -> time-major tokens [B*T, C] (contract W). */
 int eegf_window_tokens(int dtype, int B, int C, int T, const float* eeg, void* tokens, hipStream_t stream);
+/* Contract W at any length, with a step mask and a patch tokenizer (Conv1d(C, 768, kernel P, stride P)
+ * as a GEMM over rows of width C*P; no reference counterpart: the oracle's eeg_mask semantics,
+ * oracle/fusion_oracle.py encoders()).  Token j of window b covers steps jP .. jP+P-1:
+ *   tokens[row][c*P + p] = step_mask[b, jP+p] ? eeg[b, c, jP+p] : 0     (a masked step is never read)
+ * row = cu[b] + j for j < cu[b+1] - cu[b] (cu_seqlens given: packed rows, packed_rows = cu[B]) or b*L + j
+ * (cu_seqlens NULL: packed_rows = B*L), L = T / P; rows packed_rows .. total_rows-1 are written as zeros
+ * (GEMM / weight-gradient operands).  step_mask [B, T] int64, nonzero = valid (nullable: all valid).
+ * P in {1, 2, 4, 8}, T % P == 0, C <= 128.  The EEG input takes no gradient: there is no backward. */
+int eegf_window_patch_tokens(int dtype, int B, int C, int T, int P, const long long* step_mask,
+                             const int* cu_seqlens, long packed_rows, long total_rows, const float* eeg,
+                             void* tokens, hipStream_t stream);
+/* token_mask[b, j] (int64 [B, T/P]) = 1 when any of the P steps of token j is valid, else 0: the input of
+ * eegf_seq_lengths / eegf_key_bias for a window batch. */
+int eegf_window_token_mask(int B, int T, int P, const long long* step_mask, long long* token_mask,
+                           hipStream_t stream);
+/* Position rows of a packed batch: out[cu[b] + j] = pos[j] (fp32 [total_rows, width], j < len_b; rows past
+ * packed_rows zero): eegf_ln_fwd's `table` with table_period = total_rows, so the packed rows get the
+ * fp32 position add of the padded layout's row % L table.  width % 4 == 0, 16-B aligned pointers. */
+int eegf_packed_pos_rows(int B, int L, int width, const int* cu_seqlens, long packed_rows, long total_rows,
+                         const float* pos, float* out, hipStream_t stream);
 /* word-embedding gather / scatter-add (contract T; modeling_bert.py:101-102) */
 int eegf_embed_gather(int dtype, long rows, int width, const long long* ids, const float* table, void* out,
                       hipStream_t stream);
